@@ -2,9 +2,16 @@
 """Headline benchmark: dipole field-evaluations (source-target pairs) per second on the 100 000-point
 synthetic sphere of BASELINE.json (config 4: 256 patches), one process per GPU.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`value`, `ms_per_step` and the figures taken
+from HIP events inside the timed steps: `roofline`, `hbm`, `step_parts`, `per_rank`).  Everything that needs runs or
+checks of its own - the pre-check and the pipelined loop at N > 1, the G19 comparison, `sharded_driver`, `other_configs`,
+`cpu_baseline` - runs only with --full.  --dump-outputs DIR writes what the last timed step computed (rank 0's):
+DIR/interaction_matrix.npy (the gathered P x P matrix W, float64) and DIR/patch_fields_sample.npy (float32 [patches of
+the rank, 8192, 3]: the slabs dE_k at a fixed, seeded sample of 8192 points of the cloud, by original point index).
 
 A STEP is one pass of the data-parallel hot path over the cloud: every one of the 256 per-patch
 field evaluations `field_grad(pts[patch_k], pts[~patch_k])` (dnp_patch_fields_tiled_f32 - all of them in
@@ -13,18 +20,18 @@ interaction matrix rows (dnp_interactions_from_tiles) and, for N > 1, the RCCL a
 that hands every rank what the sequential greedy loop needs - IN THE LAUNCH STREAM'S ORDER, exactly as the
 product's sharded driver issues it (parallel.sharded_patch_propagation -> patch_drivers._batched_patch_propagation:
 slabs -> W rows -> synchronous parallel.gather_rows -> greedy loop; the greedy loop needs all of W, so the
-driver cannot overlap the collective with anything).  `value` and `ms_per_step` are THAT step.  At N > 1 over
-RCCL a second timed loop runs the same steps with the all-gather issued asynchronously (two in flight, each
+driver cannot overlap the collective with anything).  `value` and `ms_per_step` are THAT step.  With --full, at N > 1
+over RCCL a second timed loop runs the same steps with the all-gather issued asynchronously (two in flight, each
 overlapping the next step's pair kernel: what parallel.sharded_patch_propagation_many reaches when it is handed
 several clouds) and reports it as `value_pipelined` / `ms_per_step_pipelined` - never as `value`; the gathered
 matrix of the pipelined loop is compared with the in-order one (`pipelined_matches_in_order`).  After the timed
-steps the gathered matrix is run through the device greedy loop and compared with the REFERENCE's own trace on
-this cloud (tests/golden/G19).
+steps (--full) the gathered matrix is run through the device greedy loop and compared with the REFERENCE's own trace
+on this cloud (tests/golden/G19).
 Patches are sharded over the ranks in contiguous size-balanced blocks, so the total work is fixed
 as N grows ("strong").  Inputs are resident in HBM before the timed region.  `value` counts the
 algorithmic pairs sum_k |patch_k| * (N - |patch_k|) of all ranks per second of the slowest rank.
 
-Also printed on the same JSON line:
+Also printed on the same JSON line (sharded_driver and cpu_baseline with --full only):
   roofline      the pair kernel against the FP32 vector-ALU roofline that binds it (33 flop/pair,
                 DESIGN.md), timed by HIP events recorded INSIDE the timed steps (mean / median / min;
                 launch_ms <= ms_per_step is asserted); `hbm` carries the algorithmic HBM GB/s the metric
@@ -254,10 +261,17 @@ def main():
     # 10 untimed steps by default: the first ~8 launches after an idle period run up to 25 % slower while the clocks
     # ramp (5.3, 5.1, 4.8, 4.7, 4.6, 4.4, 4.4, 4.3 ms, then 4.26 +- 0.03; profiles/r02_kernel_trace_durations.txt)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the pre-check and the pipelined loop (N > 1), the G19 comparison, the sharded driver leg, "
+                         "the other configs and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--headline-only", action="store_true",
-                    help="skip the other_configs legs (profiling runs: only the headline kernels in the trace)")
+                    help="with --full: skip the other_configs and sharded_driver legs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -315,6 +329,13 @@ def main():
     # patch is a contiguous row range and every slab / interaction access is coalesced
     off, idx, _ = util.patch_csr(patches, dev)
     pts = pc_cpu.to(dev)[idx].contiguous()
+    dump_rows = None
+    if args.dump_outputs and rank == 0:
+        # the sampled points' rows in the patch-sorted layout (by original point index, so the sample is layout-independent)
+        sample = np.sort(np.random.default_rng(0).choice(N_POINTS, 8192, replace=False))
+        pos = torch.empty_like(idx)
+        pos[idx] = torch.arange(idx.numel(), device=dev)
+        dump_rows = pos[torch.from_numpy(sample).to(dev)]
     point_patch = torch.repeat_interleave(torch.arange(N_PATCHES, device=dev), off[1:] - off[:-1])
     idx = None
     boxes = fu._patch_boxes(pts, off, idx)       # per-cloud set-up like the CSR offsets (the drivers do the same once)
@@ -339,7 +360,7 @@ def main():
     # HIP events on the stream the kernels are launched on (torch's current stream = what _lib.current_stream() hands
     # to the C ABI), recorded INSIDE the timed steps: the pair kernel's duration, the interaction kernel's and the
     # all-gather's come from the same launches, buffers and clocks as ms_per_step
-    def step(marks=None):
+    def step(marks=None, keep=None):
         if marks is not None:
             marks[0].record()
         if tiles.fused:              # what the drivers do (patch_drivers._slabs_and_rows), opened up for the event marks
@@ -347,6 +368,8 @@ def main():
             dE = fu._patch_slabs(pts, off, idx, point_patch, p_lo, p_hi, 1e-5, boxes, tiles.boxes, w_part, split, order)
         else:
             dE = fu._patch_slabs(pts, off, idx, point_patch, p_lo, p_hi, 1e-5, boxes, tiles.boxes, None, split, order)
+        if keep is not None:         # --dump-outputs: the slabs of the last timed step
+            keep["dE"] = dE
         if marks is not None:
             marks[1].record()
         if tiles.fused:
@@ -407,9 +430,9 @@ def main():
 
     # ---- before anything is timed (N > 1; round-4 verdict: the first run with more than one RCCL rank must not be trusted
     # blindly): every rank's rows of the gathered matrix are the rows it computed, the matrix reproduces the reference's trace,
-    # and every rank answered the collective
+    # and every rank answered the collective (--full)
     precheck = None
-    if world > 1 or one_rank_rccl:
+    if args.full and (world > 1 or one_rank_rccl):
         deadline.phase = "precheck (first collectives)"
         torch.cuda.synchronize()
         w_part0 = torch.empty((p_hi - p_lo, tiles.n_tiles, tiles.slots), dtype=torch.float64, device=dev) if tiles.fused else None
@@ -472,11 +495,12 @@ def main():
         detail = world > 1 or i % 4 == 0
         return [torch.cuda.Event(enable_timing=True) if (j < 2 or detail) else None for j in range(4)]
     ev = [marks_for(i) for i in range(args.steps)]
+    last = {} if dump_rows is not None else None
     deadline.phase = "timed steps"
     fence()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        W = step(ev[i])
+        W = step(ev[i], last if i == args.steps - 1 else None)
     fence()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -485,10 +509,15 @@ def main():
         elapsed = float(tmax.item())
     ms_per_step = elapsed / args.steps * 1e3
     W_in_order = W
+    if last is not None:
+        deadline.phase = "dump outputs"
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "interaction_matrix.npy"), W.double().cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "patch_fields_sample.npy"), last.pop("dE")[:, dump_rows].float().cpu().numpy())
 
     # ---- the same steps with the all-gather overlapped (N > 1 over RCCL): reported beside the headline, never as it ---
     pipelined = None
-    if can_pipeline:
+    if args.full and can_pipeline:
         deadline.phase = "pipelined steps (asynchronous all-gather)"
         overlap_state["on"] = True
         for _ in range(max(args.warmup, 4)):
@@ -573,14 +602,14 @@ def main():
     # scrambled patch ends with one sign, every untouched patch with the other
     signs_ok = None
     trace_matches_reference = chosen_dev = None
-    if not (fake > 1 and world == 1):
+    if args.full and not (fake > 1 and world == 1):
         assert W.shape == (N_PATCHES, N_PATCHES)
         signs_ok, trace_matches_reference, chosen_dev = check_against_g19(W)
 
     # ---- N > 1: the whole product call, every rank in it (what a caller of parallel.sharded_patch_propagation gets) ------
     sharded_driver = None
     deadline.phase = "sharded driver leg / other configs"
-    if world > 1 and not args.headline_only:
+    if args.full and world > 1 and not args.headline_only:
         ranges = util.PatchList(torch.arange(N_POINTS, device=dev), sizes, disjoint=True)
         plist = list(enumerate(ranges))
 
@@ -620,8 +649,10 @@ def main():
                           "patches": N_PATCHES, "pairs_per_step": pairs_total,
                           "parallelism": f"patch-sharded x{world}, " + ("RCCL" if backend == "nccl" else backend) +
                                          " all-gather of W rows, in the launch stream's order"},
-               "roofline": roofline, "hbm": hbm, "step_parts": step_parts, "signs_ok": signs_ok,
-               "trace_matches_reference_G19": trace_matches_reference, "chosen_max_rel_dev_vs_G19": chosen_dev}
+               "roofline": roofline, "hbm": hbm, "step_parts": step_parts, "full": args.full}
+        if args.full:
+            out.update({"signs_ok": signs_ok, "trace_matches_reference_G19": trace_matches_reference,
+                        "chosen_max_rel_dev_vs_G19": chosen_dev})
         if per_rank is not None:
             out["per_rank"] = per_rank
         if precheck is not None:
@@ -648,10 +679,10 @@ def main():
         if world > 1 and backend != "nccl":
             out["rehearsal"] = (f"{backend} collectives; ranks may share a GPU (device_count "
                                 f"{torch.cuda.device_count()}): a functional rehearsal of the N>1 path, not a scaling number")
-        if world == 1 and not (fake > 1) and not args.headline_only:
+        if args.full and world == 1 and not (fake > 1) and not args.headline_only:
             ranges = util.PatchList(torch.arange(N_POINTS, device=dev), sizes, disjoint=True)
             out["other_configs"] = other_configs(dev, fu, util, pts, ranges)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(pc_cpu)
             out["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         fu.flush_warnings()

@@ -14,9 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not found")
-def test_tabled_pair_kernels_keep_their_register_and_lds_budget():
+def test_tabled_pair_kernels_keep_their_register_and_lds_budget(tmp_path):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_resources.py"), "dnp_patch.hip"], capture_output=True,
-                         text=True, timeout=600)
+                         text=True, timeout=600, env=dict(os.environ, DNP_ISA_DIR=str(tmp_path)))
     assert out.returncode == 0, out.stderr[-2000:]
     rows = {}
     for line in out.stdout.splitlines():
@@ -37,13 +37,13 @@ def test_tabled_pair_kernels_keep_their_register_and_lds_budget():
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not found")
-def test_no_pair_kernel_needs_a_private_segment():
+def test_no_pair_kernel_needs_a_private_segment(tmp_path):
     """Round 4 found every LDS-staged pair kernel with 12 bytes of scratch per lane (two of six staged scalars captured by
     reference went through the private segment: a store -> load round trip in each workgroup's prologue); the staged row
     travels by value now.  No pair kernel of the generic entry points may need scratch, and the small-call kernel
     (KT = 1, fp32) keeps its 8 wavefronts per SIMD."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_resources.py"), "dnp_field.hip"], capture_output=True,
-                         text=True, timeout=900)
+                         text=True, timeout=900, env=dict(os.environ, DNP_ISA_DIR=str(tmp_path)))
     assert out.returncode == 0, out.stderr[-2000:]
     seen = 0
     for line in out.stdout.splitlines():
@@ -58,15 +58,15 @@ def test_no_pair_kernel_needs_a_private_segment():
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not found")
-def test_exchange_hand_off_is_write_through_stores_then_a_wait_then_the_ticket():
+def test_exchange_hand_off_is_write_through_stores_then_a_wait_then_the_ticket(tmp_path):
     """Round-4 advisor: the split tail's hand-off uses relaxed agent-scope atomics only and is correct because of two target facts -
     the run terms are stored write-through (sc1) and an s_waitcnt vmcnt(0) stands between them and the ticket's atomic add
     (gfx9: vmcnt counts stores) - plus the last arriver's acquire (buffer_inv sc1) before it reads the terms back.  A compiler
     change that drops any of the three would fail silently on the GPU; it fails here."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_resources.py"), "dnp_patch.hip"], capture_output=True,
-                         text=True, timeout=600)
+                         text=True, timeout=600, env=dict(os.environ, DNP_ISA_DIR=str(tmp_path)))
     assert out.returncode == 0, out.stderr[-2000:]
-    text = open("/tmp/isa/dnp_patch.hip.s").read()
+    text = open(tmp_path / "dnp_patch.hip.s").read()
     names = re.findall(r"^(_ZN3dnp18pair_kernel_scalarIffLi0ELi2ELi0ELb1ELb1ELb1ELi\dELi4ELi4ELb1EEEvNS_8PairArgsIT_T0_EE):", text, flags=re.M)
     assert len(set(names)) == 3, names                     # the exchange-tail kernel without partials and with 2 / 3 group slots
     for name in set(names):
@@ -88,15 +88,15 @@ def test_exchange_hand_off_is_write_through_stores_then_a_wait_then_the_ticket()
 
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not found")
-def test_blocked_xie_solve_loop_waits_for_its_oldest_column_only():
+def test_blocked_xie_solve_loop_waits_for_its_oldest_column_only(tmp_path):
     """The solve kernel of the blocked ordered propagation keeps 8 corner columns in flight ACROSS the back edge of its step loop:
     the loads are hand-issued (inline asm) and every step waits with s_waitcnt vmcnt(7) (fp64: two loads per column, vmcnt(14)) -
     compiler-visible loads had made the loop header drain everything (vmcnt(0)) every 8 steps, 250 cycles per step instead of
     ~130.  Pinned here: inside the loop, one such wait and one column load per step, and no full drain."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "isa_resources.py"), "dnp_xie.hip"], capture_output=True,
-                         text=True, timeout=600)
+                         text=True, timeout=600, env=dict(os.environ, DNP_ISA_DIR=str(tmp_path)))
     assert out.returncode == 0, out.stderr[-2000:]
-    text = open("/tmp/isa/dnp_xie.hip.s").read()
+    text = open(tmp_path / "dnp_xie.hip.s").read()
     for mangled, younger, loads_per_step in (("_ZN3dnp22xie_block_solve_kernelIfEE", 7, 1), ("_ZN3dnp22xie_block_solve_kernelIdEE", 14, 2)):
         start = re.search(r"^" + mangled + r"\w*:", text, flags=re.M)
         assert start, mangled

@@ -2,7 +2,8 @@
 """Register / LDS / occupancy table of every kernel of one csrc file, from hipcc's -Rpass-analysis=kernel-resource-usage
 (compile only, no GPU): the check that goes with any edit of pair_kernel.h - the scalar-unit kernels must stay at <= 64 VGPRs
 (8 wavefronts per SIMD) and the tabled ones at 0 bytes of LDS.
-    python tools/isa_resources.py dnp_patch.hip [-DFLAG ...]          (writes the ISA to /tmp/isa/<file>.s)"""
+    python tools/isa_resources.py dnp_patch.hip [-DFLAG ...]          (writes the ISA to /tmp/isa/<file>.s)
+DNP_ISA_DIR=<dir> writes it to <dir>/<file>.s instead (the tests: a directory of their own)."""
 import os
 import re
 import subprocess
@@ -11,8 +12,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = sys.argv[1]
 flags = sys.argv[2:]
-os.makedirs("/tmp/isa", exist_ok=True)
-out = os.path.join("/tmp/isa", os.path.basename(src) + ".s")
+isa_dir = os.environ.get("DNP_ISA_DIR", "/tmp/isa")
+os.makedirs(isa_dir, exist_ok=True)
+out = os.path.join(isa_dir, os.path.basename(src) + ".s")
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "--offload-arch=gfx950", "-std=c++17", "-fno-gpu-rdc", "-fno-slp-vectorize", "-S",
        "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", *flags,
        os.path.join(ROOT, "dipole_normal_prop_amd", "csrc", src), "-o", out]
