@@ -406,7 +406,9 @@ static int run_pairs_body(const F* src, int64_t S, int64_t ld_src, const int64_t
     // far-field launches (fp32, >= 10^9 pairs, eps in range) of the scalar kernel split their work items by source
     const double n_pairs = (double)S * (double)T;
     const bool far_size = n_pairs >= DNP_K1_FAR_FROM || (n_pairs >= DNP_K1_FAR_FROM_WIDE && S >= 2 * T);
-    const bool far_candidate = sizeof(F) == 4 && DNP_K1_FAR && scalar_kernel && MODE == kField && eps > F(0) &&
+    // fp32 field below kNormEps: the normalised chain (pair_kernel.h, kNorm), without the far machinery
+    const bool norm = sizeof(F) == 4 && MODE == kField && eps > F(0) && (double)eps < kNormEps;
+    const bool far_candidate = sizeof(F) == 4 && DNP_K1_FAR && scalar_kernel && MODE == kField && eps > F(0) && !norm &&
                                far_size && far_threshold_d2((double)eps) > 0.0;
     const int split = (far_candidate && T >= (int64_t)kBlock * kKTScalar * kTilesForLarge) ? DNP_K1_SPLIT : 1;
     const Plan plan = make_plan(S, T, max_pts, NC, sizeof(double), scalar_kernel, split);
@@ -440,7 +442,7 @@ static int run_pairs_body(const F* src, int64_t S, int64_t ld_src, const int64_t
         // measured the boxes from two pre-kernels instead - a chunk table and a target-tile table as in patch mode:
         // 4452.6 against 4448.3 us at 100 000^2 on the patch-sorted cloud, no gain: with 780-source chunks the scan is
         // already amortised and the two extra launches cost what the tables save; profiles/r03_k1_tables_ab.txt.)
-        pa.far_d2 = (sizeof(F) == 8 ? n_pairs >= DNP_K1_FAR_FROM : far_size) ? (F)far_threshold_d2((double)eps, sizeof(F) == 8 ? kFarRatio64 : kFarRatio) : F(0);
+        pa.far_d2 = (sizeof(F) == 8 ? n_pairs >= DNP_K1_FAR_FROM : far_size) && !norm ? (F)far_threshold_d2((double)eps, sizeof(F) == 8 ? kFarRatio64 : kFarRatio) : F(0);
         for (int i = 0; i <= n_chunks; ++i) pa.chunk_off[i] = r.chunk_off[i];
 #ifdef DNP_BOUNDS
         pa.bnd = PairBounds{};
@@ -470,7 +472,16 @@ static int run_pairs_body(const F* src, int64_t S, int64_t ld_src, const int64_t
             hipLaunchKernelGGL((pair_kernel_scalar<F, double, MODE, KT, V, false>), grid, dim3(kBlock), 0, stream, \
                                pa);                                                                               \
     } while (0)
-        if (scalar_kernel) {
+        // (kNormV: kNorm where it can be chosen, else an instance that exists anyway - no fp64 / potential kNorm kernels)
+        constexpr int kNormV = (sizeof(F) == 4 && MODE == kField) ? kNorm : kFast;
+        if (norm) {
+            if (scalar_kernel && plan.kt == kKTScalar)
+                hipLaunchKernelGGL((pair_kernel_scalar<F, double, MODE, kKTScalar, kNormV, false>), grid, dim3(kBlock), 0, stream, pa);
+            else if (scalar_kernel)
+                hipLaunchKernelGGL((pair_kernel_scalar<F, double, MODE, 1, kNormV, false>), grid, dim3(kBlock), 0, stream, pa);
+            else if (plan.kt == kKTLds) DNP_LAUNCH_PAIR(kKTLds, kNormV);
+            else DNP_LAUNCH_PAIR(1, kNormV);
+        } else if (scalar_kernel) {
             if (plan.kt == kKTScalar) {
                 if (variant == kFast) DNP_LAUNCH_SCALAR(kKTScalar, kFast);
                 else if (variant == kNanCoinc) DNP_LAUNCH_SCALAR(kKTScalar, kNanCoinc);

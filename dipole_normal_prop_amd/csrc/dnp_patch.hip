@@ -311,8 +311,9 @@ static int patch_fields_f32(const float* pts, int64_t N, int64_t ld_pts, const i
     DNP_REQUIRE(ld_pts >= 6, "ld_pts=%lld < 6", (long long)ld_pts);
     // the tile tables belong to the scalar-unit kernel on the patch-sorted layout with the far chain on
     const bool scalar_path = !patch_idx && eps > 0.f && !DNP_FORCE_LDS;
+    const bool norm = eps > 0.f && (double)eps < kNormEps;     // the normalised chain (pair_kernel.h, kNorm)
     DNP_REQUIRE(!w_part || (scalar_path && patch_box && tile_box && kPatchFar && far_threshold_d2((double)eps) > 0.0),
-                "w_part needs the patch-sorted layout (patch_idx == NULL), eps >= 1e-30 and both box tables");
+                "w_part needs the patch-sorted layout (patch_idx == NULL), eps >= 1e-25 and both box tables");
     const int64_t t_tiles = ceil_div(N, (int64_t)kBlock * kPatchKT);
     const int64_t K = p_end - p_begin;
     DNP_REQUIRE(!patch_order || (scalar_path && K <= 65535), "patch_order needs the patch-sorted layout, eps > 0 and at most 65535 patches");
@@ -326,9 +327,6 @@ static int patch_fields_f32(const float* pts, int64_t N, int64_t ld_pts, const i
         pa.eps = eps; pa.partial = dE + k0 * N * 3;
         pa.chunk_perm = patch_order;
         pa.far_d2 = (float)far_threshold_d2((double)eps);
-#ifdef DNP_FAR_D2   // timing experiments only: force the far test (1e30f = never far, -1.f = always far)
-        pa.far_d2 = DNP_FAR_D2;
-#endif
         const hipStream_t st = (hipStream_t)stream;
 #ifdef DNP_BOUNDS
         {
@@ -339,7 +337,21 @@ static int patch_fields_f32(const float* pts, int64_t N, int64_t ld_pts, const i
             pa.bnd.n_src_rows = N; pa.bnd.n_chunk_perm = patch_order ? kn : 0; pa.bnd.err = bounds_err_buffer();
         }
 #endif
-        if (scalar_path) {
+        if (scalar_path && norm) {
+            // eps below kNormEps: the normalised chain (pair_kernel.h, kNorm), far chains and split tail off; the tabled
+            // form's grid, so that w_part comes out of the epilogue as there
+            const dim3 sgrid((unsigned)ceil_div(N, (int64_t)kTabledWaves * 64 * kPatchScalarKT), (unsigned)kn);
+            pa.w_part = w_part ? w_part + k0 * ceil_div(N, (int64_t)64 * kPatchScalarKT) * w_slots : nullptr;
+            if (w_part && w_slots == 3)
+                hipLaunchKernelGGL((pair_kernel_scalar<float, float, kField, kPatchScalarKT, kNorm, false, false, false, 3, 1, kTabledWaves>),
+                                   sgrid, dim3(kTabledWaves * 64), 0, st, pa);
+            else if (w_part)
+                hipLaunchKernelGGL((pair_kernel_scalar<float, float, kField, kPatchScalarKT, kNorm, false, false, false, 2, 1, kTabledWaves>),
+                                   sgrid, dim3(kTabledWaves * 64), 0, st, pa);
+            else
+                hipLaunchKernelGGL((pair_kernel_scalar<float, float, kField, kPatchScalarKT, kNorm, false, false, false, 0, 1, kTabledWaves>),
+                                   sgrid, dim3(kTabledWaves * 64), 0, st, pa);
+        } else if (scalar_path) {
             // patch-sorted cloud (what the drivers pass): contiguous sources -> the scalar-unit kernel
             const bool tabled = patch_box && tile_box && kPatchFar && pa.far_d2 > 0.f;
             // -k: ONE launch whose last k patches are split items with their run terms in the exchange buffer
@@ -398,7 +410,9 @@ static int patch_fields_f32(const float* pts, int64_t N, int64_t ld_pts, const i
             }
         } else {
             const dim3 grid((unsigned)t_tiles, (unsigned)kn);
-            if (eps > 0.f)
+            if (norm)
+                hipLaunchKernelGGL((pair_kernel<float, float, kField, kPatchKT, kNorm>), grid, dim3(kBlock), 0, st, pa);
+            else if (eps > 0.f)
                 hipLaunchKernelGGL((pair_kernel<float, float, kField, kPatchKT, kFast>), grid, dim3(kBlock), 0, st, pa);
             else if (eps == 0.f)
                 hipLaunchKernelGGL((pair_kernel<float, float, kField, kPatchKT, kNanCoinc>), grid, dim3(kBlock), 0, st, pa);

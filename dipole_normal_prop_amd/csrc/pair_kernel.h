@@ -272,7 +272,15 @@ template <> struct Math<double> {
 //   kRobust  any eps (also negative): explicit |r| == 0 test, rsq/rcp chain, 22 + 2 instructions.
 //   kNanCoinc  eps == 0: as kRobust, and a coincident pair yields NaN like the reference's 0/0
 //            (the leaf filter then zeroes the row, field_utils.py:112-115).
-enum PairVariant { kFast = 0, kRobust = 1, kNanCoinc = 2 };
+//   kNorm    fp32, 0 < eps < kNormEps: r^ = r rsq(|r|^2) first, as the reference does; w = rcp(|r|^3 + eps), a = (p.r^) w
+//            is applied to r^.  No product of the chain leaves the range of its pair's term, so it stays accurate where
+//            kFast's g = |r|^2 (|r|^3 + eps) nears FLT_MIN (tiny eps, close pairs).  A coincident pair contributes 0.
+//            Never on the default-eps path; the far chains stay off in its launches.
+enum PairVariant { kFast = 0, kRobust = 1, kNanCoinc = 2, kNorm = 3 };
+// Host side, fp32: below kNormEps the eps > 0 launches take kNorm.  kFast's FLT_MIN guard costs below 2^-24 relative while
+// g >= 2^-102; with g >= |r|^2 eps that holds for every pair at least 2^-27 = 7.5e-9 apart once eps >= 2^-102 / 2^-54 =
+// 2^-48 = 3.55e-15 (unit-box clouds: 2^-27 is a quarter of one fp32 ulp at 1, below any separation they can hold).
+constexpr double kNormEps = 3.552713678800501e-15;   // 2^-48
 
 template <typename F, int V>
 __device__ __forceinline__ void pair_field(F sx, F sy, F sz, F px, F py, F pz, F tx, F ty, F tz, F eps,
@@ -288,7 +296,7 @@ __device__ __forceinline__ void pair_field(F sx, F sy, F sz, F px, F py, F pz, F
         const F q = M::rcp_fast(M::fma(d2, den, M::kTiny));
         w = d2 * q;
         a = pr * q;
-    } else {
+    } else if (V != kNorm) {
         const bool coinc = (d2 == F(0));
         const F d2m = coinc ? M::kHuge : d2;
         const F inv = M::rsq(d2m);
@@ -296,6 +304,21 @@ __device__ __forceinline__ void pair_field(F sx, F sy, F sz, F px, F py, F pz, F
         w = M::rcp(M::fma(d2m, d, eps));
         if (V == kNanCoinc) w = coinc ? F(__builtin_nanf("")) : w;
         a = pr * (inv * inv * w);
+    }
+    if constexpr (V == kNorm) {
+        const bool coinc = (d2 == F(0));
+        const F inv = M::rsq(coinc ? F(1) : d2);
+        const F ux = rx * inv, uy = ry * inv, uz = rz * inv;
+        const F pu = M::fma(pz, uz, M::fma(py, uy, px * ux));
+        w = coinc ? F(0) : M::rcp(M::fma(d2, d2 * inv, eps));
+        a = pu * w;
+        ax = M::fma(a, ux, ax);
+        ay = M::fma(a, uy, ay);
+        az = M::fma(a, uz, az);
+        bx = M::fma(w, px, bx);
+        by = M::fma(w, py, by);
+        bz = M::fma(w, pz, bz);
+        return;
     }
     ax = M::fma(a, rx, ax);
     ay = M::fma(a, ry, ay);
@@ -319,16 +342,31 @@ __device__ __forceinline__ void pair_field(F sx, F sy, F sz, F px, F py, F pz, F
 #define DNP_FAR_RATIO 8e-3
 #endif
 constexpr double kFarRatio = DNP_FAR_RATIO;
-// Host side: the squared box distance from which the far chains run; 0 switches them off.  They need a normal-range
-// threshold: for a tiny eps (< 1e-30) far_d2 would admit pairs whose u^3 = rsq(d2)^3 overflows fp32 (then e = eps*inf
-// and w = NaN where the exact chain returns a finite 1/(|r|^3+eps)), so such calls keep the exact chain.
-constexpr double kFarMinEps = 1e-30;
+// Host side: the squared box distance from which the far chains run; 0 switches them off.  The fp32 far chains form
+// w * u^2 = |r|^-5, finite only for |r| > FLT_MAX^(-1/5) = 1.97e-8; a far pair is at least sqrt(far_d2) =
+// (eps / kFarRatio)^(1/3) apart, so eps >= kFarRatio * (1.97e-8)^3 = 6.1e-26 keeps every admitted pair finite.  kFarMinEps
+// = 1e-25 puts the nearest far pair at 2.32e-8, where |r|^-5 = 1.5e38 (0.44 FLT_MAX).  Smaller eps keep the exact chain.
+// (It was 1e-30 until the tiny-eps sweep of tests/test_gpu_far_tiers.py met a pair 1e-8 apart across two patch boxes at
+// eps = 1e-29: +-inf, and the leaf filter zeroed the whole target row.)
+constexpr double kFarMinEps = 1e-25;
 // fp64 (round 5): ONE far tier with the series taken to e^4 - 1/(1 + e) = 1 - e + e^2 - e^3 + e^4 - ..., truncation e^5 < 7.8e-17
 // (below half an fp64 ulp) for e = eps / |r|^3 < kFarRatio64 = 6e-4, i.e. boxes farther apart than 0.255 for eps = 1e-5: the
 // fp64 chain's second transcendental (v_rcp_f64, 16 cycles + 3 refinement instructions) becomes 4 fused multiply-adds.
-constexpr double kFarRatio64 = 6e-4;
+#ifndef DNP_FAR_RATIO64   // test builds only (tests/test_gpu_far_tiers.py: 0.2 makes a wrong far decision cost ~1e-4, not ~1e-17)
+#define DNP_FAR_RATIO64 6e-4
+#endif
+constexpr double kFarRatio64 = DNP_FAR_RATIO64;
+// DNP_TEST_FAR_D2 (test builds only, tests/test_gpu_far_tiers.py; the ONE override of the far decision): wherever the
+// product enables a far chain, far_d2 becomes this positive value instead - 1e38 = no pair is far, 1e-37 = every pair of
+// disjoint boxes is far (tier 2, or tier 1 with -DDNP_FAR2=0).  Launch form, kernel instance and summation order stay those
+// of the product, so a slab row of the product library equals the row of the variant whose tier it chose, bit for bit.
 static inline double far_threshold_d2(double eps, double ratio = kFarRatio) {
-    return eps >= kFarMinEps ? __builtin_pow(eps / ratio, 2.0 / 3.0) : 0.0;
+    const double d2 = eps >= kFarMinEps ? __builtin_pow(eps / ratio, 2.0 / 3.0) : 0.0;
+#ifdef DNP_TEST_FAR_D2
+    return d2 > 0.0 ? (double)(DNP_TEST_FAR_D2) : 0.0;
+#else
+    return d2;
+#endif
 }
 
 template <typename F>

@@ -155,16 +155,24 @@ def _exchange_drop(dev: torch.device) -> None:
 
 
 def _patch_slabs(work: torch.Tensor, off, idx, point_patch, p0: int, p1: int, eps: float, boxes=None, tile_boxes=None,
-                 w_part: Optional[torch.Tensor] = None, source_split: int = 1, order: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 w_part: Optional[torch.Tensor] = None, source_split: int = 1, order: Optional[torch.Tensor] = None,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """dE[p1 - p0, N, 3]: the fields of patches p0..p1 on every point (dnp_patch_fields_tiled_f32 / _ordered_f32).  boxes /
     tile_boxes: the per-cloud box tables of the far-field test (_patch_boxes, _tile_boxes); w_part: receives the per-tile
     interaction partials [p1 - p0, n_tiles, 2 or 3] (see _TileTables; the last dimension = the group slots per tile).
     source_split = -k: the last k ROWS of the launch as split items whose run terms travel through the exchange buffer (needs
     both box tables; without them the launch is the plain one).  order (device int32 [p1 - p0], patch-sorted layout only): the
-    patch, relative to p0, that launch row i evaluates - _launch_plan puts the longest patches first; slab k stays patch p0 + k."""
+    patch, relative to p0, that launch row i evaluates - _launch_plan puts the longest patches first; slab k stays patch p0 + k.
+    out: the slabs are written there (contiguous [p1 - p0, N, 3], the cloud's dtype and device) instead of a new tensor."""
     lib = _lib.require_device()
     N = work.shape[0]
-    dE = torch.empty((p1 - p0, N, 3), dtype=work.dtype, device=work.device)
+    if out is None:
+        dE = torch.empty((p1 - p0, N, 3), dtype=work.dtype, device=work.device)
+    else:
+        if out.shape != (p1 - p0, N, 3) or out.dtype != work.dtype or out.device != work.device or not out.is_contiguous():
+            raise ValueError(f"out: contiguous {work.dtype} [{p1 - p0}, {N}, 3] on {work.device} expected, got "
+                             f"{out.dtype} {tuple(out.shape)} on {out.device}")
+        dE = out
     ordered = order is not None and idx is None and eps > 0 and p1 - p0 <= 65535
     if work.dtype == torch.float64:
         # a float64 cloud: double-precision slabs (the fp64 far chain when both box tables are given; no split tail)
@@ -332,6 +340,10 @@ def _launch_plan(sizes_block, n_targets: int, dev, tail: bool = True):
     return order, split
 
 
+# the smallest eps of the fp32 far chains (pair_kernel.h, kFarMinEps): below it dnp_patch_fields_*_f32 refuses w_part
+FAR_MIN_EPS = 1e-25
+
+
 def _slabs_and_rows(swork, off, point_patch, b0: int, b1: int, eps: float, boxes, tiles: "_TileTables", sizes=None):
     """One evaluation of patches b0..b1 on the patch-sorted cloud: (dE[b1-b0, N, 3], W rows [b1-b0, P] fp64).  When the
     tiles allow it the interaction rows come out of the pair kernel's epilogue (+ a tiny gather kernel), otherwise from
@@ -340,7 +352,7 @@ def _slabs_and_rows(swork, off, point_patch, b0: int, b1: int, eps: float, boxes
     f64 = swork.dtype == torch.float64
     order, split = (None, 1) if sizes is None else _launch_plan(np.asarray(sizes)[b0:b1], swork.shape[0], swork.device,
                                                                tail=not (tiles is None or boxes is None or f64))
-    if tiles is not None and tiles.fused and ((boxes is not None and eps >= 1e-30) or (f64 and eps > 0)):
+    if tiles is not None and tiles.fused and ((boxes is not None and eps >= FAR_MIN_EPS) or (f64 and eps > 0)):
         lib = _lib.require_device()
         K, N = b1 - b0, swork.shape[0]
         w_part = torch.empty((K, tiles.n_tiles, tiles.slots), dtype=torch.float64, device=swork.device)

@@ -55,6 +55,24 @@ const char* dnp_last_error(void);      /* thread-local, never NULL */
  *   E[t] = - sum_s [ 3 (p_s . r^) r^ - p_s ] / (|r|^3 + eps),   r = x_s - x_t,
  *   pairs with |r| == 0 contribute 0/(0+eps) (field_utils.py:99-108).
  *
+ * Domain (the same for every entry point that evaluates this sum, the patch slabs included).  Within it a pair's term is
+ * within a few fp32 / fp64 ulps of the formula, plus the fp32 far chains' truncation (< 5.1e-7 relative; with rounding
+ * <= 1.0e-6 measured) and the fp64 one (below half an ulp).  Outside it nothing faults, but terms are wrong:
+ *   fp32, eps >= 2^-48 = 3.55e-15 (kFast): |r|^2 (|r|^3 + eps) >= 2^-102, which every |r| >= 2^-27 = 7.5e-9 meets
+ *         (1.4e-13 for eps = 1e-5).  Closer pairs show the chain's FLT_MIN guard and their term shrinks towards 0.
+ *         The far chains run only for eps >= 1e-25, so every far pair is >= 2.3e-8 apart and |r|^-5 stays finite.
+ *   fp32, 0 < eps < 2^-48 (kNorm, r^ formed first as the reference does): |r| >= 1.1e-19 (|r|^2 normal) and
+ *         |r|^3 + eps >= 3e-39.  No far chains.
+ *   fp32, eps <= 0 (kRobust, kNanCoinc): |r|^2 | |r|^3 + eps | >= 2.9e-39 (|r| >= 2.0e-8 at eps = 0); closer, the
+ *         product 1 / (|r|^2 (|r|^3 + eps)) overflows and zeroes the leaf.  The potential (K2, fp32): |r| >= 1.5e-13.
+ *   fp32 upper end, every eps: |r| < 5.3e7.  Beyond, kFast's |r|^5 overflows and the pair's term is 0; from 1.8e19
+ *         (|r|^2 = inf) it is NaN and zeroes its leaf.  The far chains lose accuracy from about 4e7 (|r|^-5 subnormal).
+ *   fp64: |r|^2 (|r|^3 + eps) >= 2^-969 (|r| >= 5e-59 as eps -> 0) and |r| < 1.6e61; beyond, the term is NaN and
+ *         zeroes its leaf.
+ *   A source row with a non-finite position (|r|^2 = inf) makes a NaN term that zeroes its leaf; the reference gives 0.
+ * The callers normalise every cloud to the unit box (util.Transform), well inside every edge.  tests/test_gpu_far_tiers.py
+ * checks each chain per eps decade up to these edges (test_every_chain_per_eps_decade, test_tiny_eps_pairs_across_patch_faces).
+ *
  * max_pts > 0 reproduces the reference's recursion semantics (field_utils.py:73-94): the
  * source range is halved at int(n/2) until every leaf has <= max_pts rows; each leaf sum has
  * its Inf/NaN components zeroed (field_utils.py:110-115) before the leaves are added.
@@ -193,7 +211,7 @@ int dnp_patch_fields_boxed_f32(const float* pts, int64_t N, int64_t ld_pts,
  * again, and a record's place in the buffer depends on its (patch, tile) index only, so one buffer serves launches of any
  * size one after the other - on ONE stream at a time.  A launch with source_split < 0 and no (or too small a) buffer
  * returns DNP_EWORKSPACE.
- * dE is bit-identical with dnp_patch_fields_boxed_f32's; w_part requires eps >= 1e-30 and both tables.
+ * dE is bit-identical with dnp_patch_fields_boxed_f32's; w_part requires eps >= 1e-25 (the far chains' range) and both tables.
  */
 int64_t dnp_patch_tile_rows(void);
 int dnp_tile_boxes_f32(const float* pts, int64_t N, int64_t ld_pts, int64_t rows_per_tile, float* boxes, void* stream);

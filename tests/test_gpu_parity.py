@@ -482,8 +482,9 @@ def test_launch_order_does_not_change_a_bit(dev, dtype):
             order = t(perm.astype(np.int32)).to(dev)
             for ss in ((1, -1, -3, -K) if dtype == torch.float32 else (1,)):
                 wp = torch.full((K, tl.n_tiles, slots), float("nan"), dtype=torch.float64, device=dev) if slots else None
-                torch.full((K, sw.shape[0], 3), float("nan"), dtype=dtype, device=dev)
-                got = fu._patch_slabs(sw, of, None, pp, p0, p1, 1e-5, bx, tl.boxes, wp, ss, order)
+                poisoned = torch.full((K, sw.shape[0], 3), float("nan"), dtype=dtype, device=dev)
+                got = fu._patch_slabs(sw, of, None, pp, p0, p1, 1e-5, bx, tl.boxes, wp, ss, order, out=poisoned)
+                assert got.data_ptr() == poisoned.data_ptr()
                 assert torch.equal(got, ref), (perm[:4], ss)
                 assert slots == 0 or torch.equal(wp, wp0), (perm[:4], ss)
 
